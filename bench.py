@@ -331,6 +331,36 @@ def feed_beside_step(step, args, dev, first_index):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+DUMP_SAMPLE = 1 << 16          # elements kept per weight tensor by --dump-outputs (all of them when the tensor is smaller)
+DUMP_BUDGET = 64 << 20         # bytes, every file of one dump together
+
+
+def dump_outputs(out_dir, loss, optimizer, model):
+    """--dump-outputs: what the timed step hands back -- its loss, the gradient norm the optimiser step used, and the
+    weights it updated (parameters and their EMA) -- as <out_dir>/<name>.npy.  Weight tensors larger than DUMP_SAMPLE
+    elements are sampled at sorted positions drawn from a generator seeded by the tensor's name, so two runs or two
+    builds with the same arguments dump the same elements."""
+    import zlib
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": loss.double().reshape(1), "grad_norm": optimizer.grad_norm.double().reshape(1)}
+    ema = optimizer.ema_tensors() if optimizer.flat_ema is not None else {}
+    for name, p in model.named_parameters():
+        n = p.numel()
+        idx = None
+        if n > DUMP_SAMPLE:
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = torch.from_numpy(np.sort(rng.choice(n, DUMP_SAMPLE, replace=False))).to(p.device)
+        for prefix, t in (("param", p), ("ema", ema.get(p))):
+            if t is not None:
+                flat = t.detach().reshape(-1)
+                arrays[f"{prefix}.{name}"] = (flat if idx is None else flat[idx]).float()
+    total = sum(a.numel() * a.element_size() for a in arrays.values())
+    assert total <= DUMP_BUDGET, f"--dump-outputs: {total} bytes over the {DUMP_BUDGET} byte budget"
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -366,7 +396,12 @@ def main():
     ap.add_argument("--feed", action="store_true",
                     help="after the timed loop, time the same steps again WHILE the data feed (AudioBatchLoader: 8 FLAC decode "
                          "threads, side-stream log-mel / normalise / splice kernels) produces one batch per step (N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed loop, write what its last step computed (loss, gradient norm, a seeded sample of the "
+                         "updated weights and EMA weights) as DIR/<name>.npy: outputs of two builds compare file by file")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args.gpus)     # nothing in this process has touched the GPU yet
@@ -591,6 +626,9 @@ def main():
     elapsed = time.perf_counter() - t0
     _lib.timing.enabled = False
     log(f"{args.steps} timed steps in {elapsed:.3f} s")
+    if args.dump_outputs and rank == 0:   # before --feed / --launch-sources run more steps over the same model
+        dump_outputs(args.dump_outputs, last_loss, optimizer, model)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
     exposed_ms = reducer.exposed_ms() / args.steps if reducer is not None else 0.0
     stats = torch.tensor([elapsed, audio_s, exposed_ms], dtype=torch.float64, device=dev)

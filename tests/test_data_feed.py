@@ -305,9 +305,7 @@ def test_wav_decode_formats_and_batch(tmp_path):
 def test_tokenizer_roundtrip():
     from caiman_asr_amd.data.tokenizer import Tokenizer
 
-    spm_path = "/root/reference/training/tests/test_data/librispeech29.model"
-    if not os.path.exists(spm_path):
-        pytest.skip("sentencepiece model of the reference's test data is not on this machine")
+    spm_path = os.path.join(GOLD, "librispeech29.model")   # the reference's test-data sentencepiece model
     tok = Tokenizer(labels=list(" abcdefghijklmnopqrstuvwxyz'"), sentpiece_model=spm_path)
     ids = tok.tokenize("the cat  sat")
     assert tok.num_labels == 29 and 0 not in ids and tok.detokenize(ids) == "the cat sat" and tok.detokenize(0) == "⁇"
